@@ -8,7 +8,12 @@ weak scaling).  Inputs are generated on each device before the timed region
 (counter-based stream, seed 11), so they are resident in HBM when timing starts.
 Rank 0 prints ONE JSON line.
 
-Extra fields: SKS on the same inputs (configs[2]), TensorACA rect at B = 64 K
+A plain run does only that: it sets up, warms up, times the K steps, writes the last step's
+H if --dump-outputs DIR is given (DIR/H.npy, float32 or float64; a fixed seeded sample of the
+rows above DUMP_MAX_BYTES; the inputs are the same in every run with the same arguments) and
+prints the line.  Everything below runs with --full only.
+
+Extra fields (--full): SKS on the same inputs (configs[2]), TensorACA rect at B = 64 K
 (configs[3]) against the torch-composed formulation on the same GPU, a streaming
 copy yardstick, the roofline of the dominant kernel and the CPU baseline (the
 reference's own C++ solver bodies, timed on this host's cores).
@@ -59,8 +64,17 @@ def parse():
     ap.add_argument("--dtype", default="f32", choices=["f32", "f64"])
     ap.add_argument("--seed", type=int, default=SEED, help="input stream seed")
     ap.add_argument("--rect-batch", type=int, default=65536)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline")
-    ap.add_argument("--no-extras", action="store_true", help="ACA headline only")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything reported beside it (the "
+                         "per-launch distribution, SKS / GE / TensorACA / Table 8 / RANSAC / host "
+                         "sections, the N>1 split / gather, the CPU baseline); a plain run sets "
+                         "up, warms up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/H.npy (the rows of a "
+                         "fixed, seeded sample when the whole H is larger than DUMP_MAX_BYTES)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full: skip the sections after the headline")
     ap.add_argument("--no-gather", action="store_true",
                     help="N>1: skip the timed split (scatter) / gather through rank 0")
     ap.add_argument("--gather-deadline", type=float, default=180.0,
@@ -74,7 +88,10 @@ def parse():
                     help="skip the shared-memory host-resident batch (per-rank zero-copy)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo only to rehearse N>1 on a one-GPU box")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps takes at least 1 timed step, --warmup at least 0")
+    return args
 
 
 def launch_plan(gpus: int, env) -> tuple[str, str]:
@@ -1601,6 +1618,37 @@ def rank_block_inputs(pkg, dev, n: int, n_total: int, rank: int):
     return src, tar
 
 
+# --dump-outputs: at most this much of H is written (the headline's 10 M x 9 f32 is 360 MB)
+DUMP_MAX_BYTES = 48 << 20
+DUMP_SAMPLE_SEED = 20250101
+
+
+def dump_rows(n: int, row_bytes: int):
+    """The problems whose H --dump-outputs writes: all n while they fit in DUMP_MAX_BYTES,
+    otherwise a fixed sample of them (numpy's PCG64 seeded with DUMP_SAMPLE_SEED, drawn
+    without replacement, ascending) -- the same rows for the same n and dtype in every run
+    and every build, so two dumps compare element for element.  None means all."""
+    rows = DUMP_MAX_BYTES // row_bytes
+    if n <= rows:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=rows, replace=False))
+
+
+def dump_outputs(path: str, H, layout: str) -> dict:
+    """Writes the headline's output buffer as it stands -- the H of the last timed step, what
+    a caller of pkg.solve(..., out=H) receives -- to path/H.npy in its own dtype (float32 or
+    float64) and layout ((rows, 9) AoS, (9, rows) SoA); returns what it wrote."""
+    axis = 1 if layout == "soa" else 0
+    n = H.shape[axis]
+    rows = dump_rows(n, 9 * H.element_size())
+    got = H if rows is None else H.index_select(axis, torch.from_numpy(rows).to(H.device))
+    got = got.contiguous().cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "H.npy"), got)
+    return {"file": "H.npy", "shape": list(got.shape), "dtype": str(got.dtype),
+            "rows": "all" if rows is None else f"{len(rows)} of {n} (seed {DUMP_SAMPLE_SEED})"}
+
+
 def main():
     args = parse()
     # --gpus N is authoritative: a bare `bench.py --gpus 8` starts the 8 ranks itself, and a
@@ -1641,7 +1689,8 @@ def main():
     # a card handed over while a previous process's device memory is still coming back:
     # wait for it before allocating and timing (one rank per GPU only -- gloo rehearsal ranks
     # share a card, and each other's memory is not foreign)
-    card = wait_quiet_card(d.dev) if d.backend == "nccl" else None
+    # (a plain run, which keeps its time outside the steps short, waits 5 s at the most)
+    card = wait_quiet_card(d.dev, 30.0 if args.full else 5.0) if d.backend == "nccl" else None
     global SEED
     SEED = args.seed
     n = args.n
@@ -1660,7 +1709,7 @@ def main():
     head_norm = head_layout == "aos"
     default_head = (head_algo, head_layout, head_dtype) == ("aca", "aos", "f32")
     if default_head:
-        run_head = run("aca")
+        run_head, hH = run("aca"), H
     else:
         hs = src.double() if head_dtype == "f64" else src
         ht = tar.double() if head_dtype == "f64" else tar
@@ -1676,7 +1725,10 @@ def main():
         run_head()
     wall, ms_launch = timed_region(d, run_head, args.steps)
     value = n_total * args.steps / wall / 1e6
-    per_launch = launch_stats(d, run_head)
+    # the last timed step's H, before anything else writes the buffer (rank 0's block)
+    dumped = (dump_outputs(args.dump_outputs, hH, head_layout)
+              if args.dump_outputs and d.rank == 0 else None)
+    per_launch = launch_stats(d, run_head) if args.full else None
     achieved = n * bpp_head / (ms_launch * 1e-3) / 1e9
     # the committed PMC figures are per launch at the bench's 10 M; another size has none
     traffic = (pmc_traffic(f"{head_algo}_{head_dtype}_{head_layout}_norm")
@@ -1722,8 +1774,11 @@ def main():
             "algorithmic_bytes_per_launch": n * bpp_head,
             "launch_ms": round(ms_launch, 5),
         },
-        "launch_stats": per_launch,
     }
+    if per_launch is not None:
+        line["launch_stats"] = per_launch
+    if dumped is not None:
+        line["dumped_outputs"] = dumped
     m = numa.get("bdf_matches_device")
     rows = d.gather_rows([numa["node"] if numa["node"] is not None else -1,
                           numa["bound_cpus"] or 0, -1 if m is None else int(m)])
@@ -1767,8 +1822,10 @@ def main():
         sys.stderr.flush()
         os._exit(EXIT_STALLED)  # the line is out; the exit code still says the run stalled
 
-    threading.Thread(target=extras_watchdog, daemon=True).start()
-    if not args.no_extras:
+    # A plain run ends here with the headline line; --full goes on to the sections below.
+    if args.full:
+        threading.Thread(target=extras_watchdog, daemon=True).start()
+    if args.full and not args.no_extras:
         try:
             if d.rank == args.inject_extras_failure:
                 raise RuntimeError("injected failure (--inject-extras-failure)")
@@ -2046,7 +2103,7 @@ def main():
         except Exception as e:  # noqa: BLE001 -- recorded, the headline still prints
             line["extras_error"] = f"{type(e).__name__}: {e}"
 
-    if d.world > 1 and not args.no_gather and "extras_error" not in line:
+    if args.full and d.world > 1 and not args.no_gather and "extras_error" not in line:
         run("aca")()
         # The split / gather is reported beside the measurement, never part of it: should its
         # point-to-point traffic stall, every rank's watchdog ends the job after the deadline
@@ -2070,7 +2127,7 @@ def main():
             line["split_gather"] = {"error": f"{type(e).__name__}: {e}"}
         done.set()
 
-    if d.rank == 0 and d.world == 1 and not args.no_cpu:
+    if args.full and d.rank == 0 and d.world == 1 and not args.no_cpu:
         try:
             line["cpu_baseline"] = cpu_baseline(min(n, 10_000_000))
             line["cpu_baseline"]["config0_n1000"] = config0_check(pkg, d.dev)
@@ -2084,7 +2141,8 @@ def main():
                 nat["gpu_speedup"] = round(line["value"] / nat["aca_value"], 1)
         except Exception as e:  # noqa: BLE001
             line["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"}
-    line["baseline_configs"] = baseline_configs(line, args, d.world)  # last: the driver's tail
+    if args.full:  # last: a tail of the line shows every BASELINE config
+        line["baseline_configs"] = baseline_configs(line, args, d.world)
     all_done.set()
     emit()
     d.close()

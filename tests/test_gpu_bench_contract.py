@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 def test_bench_line_contract():
     n, steps, warm = 200_000, 10, 2
     r = subprocess.run([sys.executable, "bench.py", "--problems-per-gpu", str(n), "--steps", str(steps),
-                        "--warmup", str(warm), "--no-extras"],
+                        "--warmup", str(warm), "--full", "--no-extras"],
                        cwd=ROOT, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
@@ -26,7 +26,8 @@ def test_bench_line_contract():
     base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
     assert d["metric"] == base["metric"]
     for k in ("value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
-              "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
+              "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline",
+              "launch_stats", "baseline_configs"):
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == steps and d["warmup"] == warm
     assert d["higher_is_better"] is True and d["scaling"] == "weak" and d["vs_baseline"] is None
@@ -43,6 +44,42 @@ def test_bench_line_contract():
         assert k in cb, k
     assert cb["kind"] == "reference" and cb["cores"] >= 1 and cb["all_core_output_bit_exact"]
     assert d["numa"]["per_rank"][0]["rank"] == 0
+
+
+def test_plain_run_is_headline_only_and_dumps_last_step(pkg, dev, tmp_path):
+    """Without --full the line is the headline alone (none of the sections that take runs of
+    their own), and --dump-outputs writes the last timed step's H: float32, the fixed seeded
+    sample of rows (the batch is past DUMP_MAX_BYTES), bit for bit what pkg.solve gives on the
+    same inputs."""
+    import numpy as np
+    import torch
+
+    import bench
+    n, steps, warm = 1_500_000, 3, 1
+    assert n * 36 > bench.DUMP_MAX_BYTES
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--problems-per-gpu", str(n),
+                        "--steps", str(steps), "--warmup", str(warm), "--dump-outputs", str(tmp_path)],
+                       cwd=ROOT, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
+    assert d["metric"] == base["metric"] and d["unit"] == "M homographies/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32" and d["steps"] == steps
+    assert abs(d["value"] - n / d["ms_per_step"] / 1e3) / d["value"] < 0.01
+    for k in ("launch_stats", "reference_statistic", "sks", "ge_baseline", "tensor_aca_rect",
+              "ransac", "host_boundary", "cpu_baseline", "baseline_configs", "extras_error"):
+        assert k not in d, k
+    assert sorted(os.listdir(tmp_path)) == ["H.npy"]
+    got = np.load(tmp_path / "H.npy")
+    rows = bench.dump_rows(n, 36)
+    assert got.dtype == np.float32 and got.shape == (len(rows), 9) and got.nbytes <= 64 << 20
+    assert d["dumped_outputs"]["shape"] == [len(rows), 9]
+    assert np.array_equal(rows, bench.dump_rows(n, 36)) and np.all(np.diff(rows) > 0)
+    src, tar = bench.rank_block_inputs(pkg, dev, n, n, 0)
+    want = pkg.solve("aca", src, tar, normalize=True)[torch.from_numpy(rows).to(dev)].cpu().numpy()
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
 
 
 @pytest.mark.parametrize("algo,layout,dtype,bpp", [("sks", "aos", "f32", 100), ("gpt", "soa", "f64", 200)])

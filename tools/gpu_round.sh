@@ -71,7 +71,7 @@ for step in $STEPS; do
         gpus2_bare)
             # the driver-shaped bare command with --gpus 2 and no torchrun: bench.py starts the
             # two ranks itself (gloo: they share the one GPU here) and prints n_gpus 2
-            run gpus2_bare 400 python bench.py --gpus 2 --steps 20 --warmup 2 --no-extras \
+            run gpus2_bare 400 python bench.py --gpus 2 --steps 20 --warmup 2 --full --no-extras \
                 --dist-backend gloo ;;
         prof_rect_bwd) run prof_rect_bwd 300 rocprofv3 --kernel-trace --stats --output-format csv \
                 -d "$OUT/prof_rect_bwd_$TAG" -o run -- python3 tools/prof_rect_bwd.py ;;
@@ -88,10 +88,10 @@ for step in $STEPS; do
                 -d "$OUT/tests_prof_$TAG" -o run -- python3 -u -m pytest tests -m gpu -x -v \
                 -p no:cacheprovider --timeout 300 --timeout-method thread
             gzip -f "$OUT/tests_prof_$TAG"/*kernel_trace.csv 2>/dev/null || true ;;
-        bench) run bench 600 python bench.py ;;
+        bench) run bench 600 python bench.py --full ;;
         prof)
             run prof 900 rocprofv3 --kernel-trace --stats --output-format csv \
-                -d "$OUT/prof_$TAG" -o run -- python3 bench.py --no-cpu
+                -d "$OUT/prof_$TAG" -o run -- python3 bench.py --full --no-cpu
             # the per-launch trace (~50 K launches) is reduced here and compressed, so the
             # session's output stays under gpurun's 64 MiB copy-back limit
             grep '^{' "$OUT/prof.log" > "$OUT/prof_$TAG/bench_line.json" || true
@@ -190,37 +190,37 @@ for step in $STEPS; do
             # 2 ranks sharing the one GPU over gloo; the real N>1 run uses RCCL
             run dist2 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
                 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 20 \
-                --warmup 2 --no-extras --dist-backend gloo ;;
+                --warmup 2 --full --no-extras --dist-backend gloo ;;
         dist4)
             # four ranks over gloo on the one GPU (the split / gather with 3 peers)
             run dist4 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 \
                 --master-addr 127.0.0.1 --master-port 29521 bench.py --gpus 4 --steps 10 \
-                --warmup 2 --no-extras --dist-backend gloo ;;
+                --warmup 2 --full --no-extras --dist-backend gloo ;;
         dist2_full)
             # the driver's N>1 command as it runs it (every extra section on), 2 ranks sharing
             # the one GPU over gloo: all sections keep the ranks in step to the one JSON line
             run dist2_full 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
                 --master-addr 127.0.0.1 --master-port 29525 bench.py --gpus 2 --steps 20 \
-                --warmup 2 --dist-backend gloo ;;
+                --warmup 2 --full --dist-backend gloo ;;
         dist2_fail)
             # the extras guard: rank 1 fails as the extras start; rank 0 must still print the
             # headline line (with extras_error) -- directly or through the extras watchdog
             run dist2_fail 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
                 --master-addr 127.0.0.1 --master-port 29527 bench.py --gpus 2 --steps 20 \
-                --warmup 2 --dist-backend gloo --inject-extras-failure 1 --extras-deadline 60 ;;
+                --warmup 2 --full --dist-backend gloo --inject-extras-failure 1 --extras-deadline 60 ;;
         dist2_deadline)
             # the split / gather watchdog: a deadline too short to meet ends every rank and
             # rank 0 still prints the measured line, with the stall recorded
             run dist2_deadline 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
                 --master-addr 127.0.0.1 --master-port 29523 bench.py --gpus 2 --steps 20 \
-                --warmup 2 --no-extras --dist-backend gloo --gather-deadline 0.001 ;;
+                --warmup 2 --full --no-extras --dist-backend gloo --gather-deadline 0.001 ;;
         dist8_small)
             # eight gloo ranks sharing the one GPU, every section on, 1 M problems per rank: the
             # N = 8 control path end to end (NUMA records, split / gather with 7 peers, the
             # host-sharded batch allocated by 8 ranks) in a few minutes
             run dist8_small 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
                 --master-addr 127.0.0.1 --master-port 29531 bench.py --gpus 8 --steps 20 \
-                --warmup 2 --problems-per-gpu 1000000 --dist-backend gloo --extras-deadline 500 ;;
+                --warmup 2 --full --problems-per-gpu 1000000 --dist-backend gloo --extras-deadline 500 ;;
         torchrun1)
             run torchrun1 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
                 --master-addr 127.0.0.1 --master-port 29519 bench.py --gpus 1 --steps 50 \
