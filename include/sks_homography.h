@@ -252,6 +252,44 @@ int hg_sample_solve_seeded_f32(const float* pool_src, const float* pool_tar, uin
 int hg_ransac_score_f32(const float* H, int64_t n, const float* pool_src, const float* pool_tar,
                         uint32_t npool, float thresh, uint32_t* counts, void* stream);
 
+/* ---- Batched RANSAC consensus (hg_consensus.hip); added after 0.3 ----
+ * For each of `pairs` image pairs: draw, solve, score and reduce n hypotheses on the device
+ * and return the pair's best homography, its inlier count, the winning index and the inlier
+ * mask.  No per-hypothesis data reaches memory and the host is not involved.
+ *
+ * pool_src / pool_tar: (total,2) correspondences of all pairs back to back (8-B aligned);
+ * pair_offsets: pairs + 1 row offsets ON THE DEVICE (8-B aligned): pair j owns rows
+ * [pair_offsets[j], pair_offsets[j+1]), m_j of them.  Offsets are clamped into [0, total] on
+ * the device; a pair with pair_offsets[j+1] <= pair_offsets[j] is empty: best_count 0,
+ * best_index 0, best_H nine quiet NaNs (0x7FC00000), no mask byte written.
+ *
+ * Hypothesis i of pair j takes words offset + 4 (j n + i) ... + 3 of hg_fill_bits_u32's
+ * stream for `seed`, each reduced modulo m_j.  Its H is row i of
+ * hg_sample_solve_seeded_f32(pool_j, m_j, seed, offset + 4 n j, ..., HG_FLAG_NORMALIZE), its
+ * count hg_ransac_score_f32's; the winner is the largest count, ties to the lowest i.  So
+ * best_H (pairs,9; 4-B aligned), best_count (pairs) and best_index (pairs) equal that
+ * unfused path pair by pair, bit for bit (when every H is NaN: index 0, row 0's NaN bits).
+ * mask: (total) bytes, mask[r] = 1 when row r is an inlier of its pair's best_H, else 0;
+ * rows that no pair owns are not written; NULL skips it.
+ *
+ * workspace: hg_ransac_consensus_workspace(pairs, n) bytes of device scratch, 8-B aligned
+ * (that function computes on the host and returns 0 for a shape the call refuses).
+ * 1 <= n <= 2^31, 0 <= total < 2^31, pairs < 2^20; pairs == 0 is a no-op.  Two kernel
+ * launches in a chain on `stream`: nothing allocated, no synchronisation, capturable in a
+ * hipGraph, deterministic.  algo 0 = ACA, 1 = SKS. */
+int64_t hg_ransac_consensus_workspace(int64_t pairs, int64_t n);
+int hg_ransac_consensus_f32(const float* pool_src, const float* pool_tar, int64_t total,
+                            const int64_t* pair_offsets, int64_t pairs, int64_t n, float thresh,
+                            uint64_t seed, uint64_t offset, int algo, float* best_H,
+                            uint32_t* best_count, int64_t* best_index, uint8_t* mask,
+                            void* workspace, void* stream);
+
+/* The mask step on its own: mask[i] = 1 when point i is an inlier of H (9 floats on the
+ * device, 4-B aligned) by hg_ransac_score_f32's test, else 0.  mask: (npool) bytes.
+ * Added after 0.3. */
+int hg_ransac_inlier_mask_f32(const float* H, const float* pool_src, const float* pool_tar,
+                              uint32_t npool, float thresh, uint8_t* mask, void* stream);
+
 /* ---- The reference's Table-8 sampling pipeline in its own formats (hg_table8.hip) ----
  * GPU_Runtime Test.cu:1443-1451: 4*n MRG32K3A words, get_rand_list, cal_ACA/cal_SKS.
  * rand_list is (4,n) uint32 -- word k of hypothesis id at rand_list[id + k*n], as

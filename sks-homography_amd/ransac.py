@@ -240,7 +240,10 @@ class RansacResult(NamedTuple):
 def ransac(pool_src: torch.Tensor, pool_tar: torch.Tensor, hypotheses: int, thresh: float,
            seed: int = 11, algo: str = "aca") -> RansacResult:
     """Draws ``hypotheses`` random 4-point samples and solves them (one fused launch),
-    scores them all and returns the best (ties: lowest index)."""
+    scores them all and returns the best (ties: lowest index).  The winner is read back
+    through the host; ``ransac_consensus`` gives the same H, count and index -- for many
+    image pairs in one call, with the inlier mask, without a host round trip -- when the
+    per-hypothesis counts are not needed."""
     _require_device(pool_src, pool_tar)
     if hypotheses < 1:
         raise ValueError(f"ransac needs at least one hypothesis, got {hypotheses}")
@@ -248,3 +251,94 @@ def ransac(pool_src: torch.Tensor, pool_tar: torch.Tensor, hypotheses: int, thre
     counts = score(H, pool_src, pool_tar, thresh)
     best = int((counts == counts.max()).nonzero()[0].item())
     return RansacResult(H[best].clone(), int(counts[best].item()), best, counts)
+
+
+class ConsensusResult(NamedTuple):
+    H: torch.Tensor          # (pairs,9) float32: best hypothesis of each pair (normalised)
+    inliers: torch.Tensor    # (pairs,) int32: its inlier count
+    index: torch.Tensor      # (pairs,) int64: which hypothesis won (ties: lowest)
+    mask: torch.Tensor       # (total,) uint8: 1 where a pool row is an inlier of its pair's H
+
+
+def _pair_pools(pool_src: torch.Tensor, pool_tar: torch.Tensor):
+    for p in (pool_src, pool_tar):
+        if p.dim() != 2 or p.shape[1] != 2:
+            raise ValueError(f"pool must be (npool,2), got {tuple(p.shape)}")
+    if pool_src.shape[0] != pool_tar.shape[0]:
+        raise ValueError("pool_src and pool_tar must hold the same number of points, got "
+                         f"{pool_src.shape[0]} and {pool_tar.shape[0]}")
+    if pool_src.shape[0] >= 1 << 31:
+        raise ValueError("the pools must hold fewer than 2^31 points")
+
+
+def ransac_consensus(pool_src: torch.Tensor, pool_tar: torch.Tensor, hypotheses: int,
+                     thresh: float, pair_offsets=None, seed: int = 11, offset: int = 0,
+                     algo: str = "aca", mask: bool = True) -> ConsensusResult:
+    """RANSAC consensus of many image pairs in one device pass (hg_ransac_consensus_f32).
+
+    The pools hold every pair's correspondences back to back; pair j owns rows
+    ``pair_offsets[j]:pair_offsets[j+1]`` (a list, or an int64 tensor -- a host one is moved to
+    the device once; None: one pair, the whole pool).  For each pair, ``hypotheses`` samples
+    are drawn, solved, scored and reduced on the device: (H, inliers, index) equal
+    ``ransac(pool_j, ..)`` made with stream offset ``offset + 4 * hypotheses * j``, bit for
+    bit, and ``mask`` marks the pair's inliers of its H (all zero when ``mask=False``).  An
+    empty pair gives NaN H, 0 inliers, index 0.  Everything returned is a device tensor;
+    nothing synchronises, so the call can be captured in a graph."""
+    _pair_pools(pool_src, pool_tar)
+    if algo not in ("aca", "sks"):
+        raise ValueError(f"algo must be 'aca' or 'sks', got {algo!r}")
+    if not 1 <= hypotheses <= 1 << 31:
+        raise ValueError(f"hypotheses must be in [1, 2^31], got {hypotheses}")
+    total = pool_src.shape[0]
+    if pair_offsets is None:
+        pair_offsets = [0, total]
+    if not isinstance(pair_offsets, torch.Tensor):
+        pair_offsets = torch.tensor([int(v) for v in pair_offsets], dtype=torch.int64)
+    # offsets known on the host that rise from <= 0 to >= total give every row to one pair:
+    # the kernel then writes the whole mask, and it need not be cleared first
+    tiled = False
+    if mask and pair_offsets.dim() == 1 and pair_offsets.numel() and not pair_offsets.is_cuda:
+        v = pair_offsets.tolist()
+        tiled = v[0] <= 0 and v[-1] >= total and all(a <= b for a, b in zip(v, v[1:]))
+    if pair_offsets.dim() != 1 or pair_offsets.numel() < 1 or pair_offsets.dtype != torch.int64:
+        raise ValueError("pair_offsets must be a 1-D int64 tensor (or a list) of pairs + 1 "
+                         f"offsets, got {tuple(pair_offsets.shape)} {pair_offsets.dtype}")
+    dev = _require_device(pool_src, pool_tar)
+    if pair_offsets.device != dev:
+        if pair_offsets.is_cuda:
+            raise ValueError(f"tensors on different devices: {dev} vs {pair_offsets.device}")
+        pair_offsets = pair_offsets.to(dev)
+    off = pair_offsets.contiguous()
+    pairs = off.numel() - 1
+    ps, pt = _pool(pool_src), _pool(pool_tar)
+    H = torch.empty((pairs, 9), dtype=torch.float32, device=dev)
+    inliers = torch.empty(pairs, dtype=torch.int32, device=dev)
+    index = torch.empty(pairs, dtype=torch.int64, device=dev)
+    out_mask = (torch.empty if tiled else torch.zeros)(total, dtype=torch.uint8, device=dev)
+    need = _lib.lib().hg_ransac_consensus_workspace(pairs, hypotheses)
+    if need <= 0:
+        raise ValueError(f"{pairs} pairs x {hypotheses} hypotheses is beyond one call")
+    work = torch.empty(need // 8, dtype=torch.int64, device=dev)
+    with _guard(dev):
+        _lib.call("hg_ransac_consensus_f32", ps.data_ptr(), pt.data_ptr(), total, off.data_ptr(),
+                  pairs, hypotheses, float(thresh), seed, offset, 0 if algo == "aca" else 1,
+                  H.data_ptr(), inliers.data_ptr(), index.data_ptr(),
+                  out_mask.data_ptr() if mask else None, work.data_ptr(), _stream(dev))
+    return ConsensusResult(H, inliers, index, out_mask)
+
+
+def inlier_mask(H: torch.Tensor, pool_src: torch.Tensor, pool_tar: torch.Tensor,
+                thresh: float) -> torch.Tensor:
+    """(npool,) uint8: 1 where a correspondence is an inlier of the one homography ``H``
+    (9 elements, on the device) by ``score``'s test -- ``score`` of one-point pools."""
+    _pair_pools(pool_src, pool_tar)
+    if H.numel() != 9:
+        raise ValueError(f"H must hold 9 elements, got {tuple(H.shape)}")
+    dev = _require_device(H, pool_src, pool_tar)
+    H = H.reshape(9).to(torch.float32).contiguous()
+    ps, pt = _pool(pool_src), _pool(pool_tar)
+    out = torch.empty(ps.shape[0], dtype=torch.uint8, device=dev)
+    with _guard(dev):
+        _lib.call("hg_ransac_inlier_mask_f32", H.data_ptr(), ps.data_ptr(), pt.data_ptr(),
+                  ps.shape[0], float(thresh), out.data_ptr(), _stream(dev))
+    return out
