@@ -290,6 +290,55 @@ int hg_ransac_consensus_f32(const float* pool_src, const float* pool_tar, int64_
 int hg_ransac_inlier_mask_f32(const float* H, const float* pool_src, const float* pool_tar,
                               uint32_t npool, float thresh, uint8_t* mask, void* stream);
 
+/* ---- Least-squares refit of the consensus inliers (hg_refit.hip); added after 0.3 ----
+ * The step after the consensus: for each pair, H refitted to ALL rows its mask selects by the
+ * N-point DLT of the reference's runKernel_DLT baseline (C++ Codes/modules/DLT.cpp:53-119,
+ * OpenCV's kernel): centroid and mean-absolute-deviation normalisation, the Lx / Ly rows, LtL.
+ *
+ * Pools, pair_offsets, clamping and empty pairs exactly as hg_ransac_consensus_f32.  The
+ * selected set S of pair j is its rows whose mask byte is non-zero (any non-zero byte).
+ * Everything is binary64 arithmetic on the binary32 pool values, every operation rounded on
+ * its own (no contraction), only + - * / fabs:
+ *   1. n = |S|
+ *   2. c = sum over S of (x, y, u, v) / n
+ *   3. d = sum over S of |. - c| per coordinate, s = n / d
+ *   4. X = (x - c0) s0, Y = (y - c1) s1, a = (u - c2) s2, b = (v - c3) s3
+ *   5. Lx = [X, Y, 1, 0, 0, 0, -aX, -aY, -a], Ly = [0, 0, 0, X, Y, 1, -bX, -bY, -b],
+ *      LtL[j][k] += Lx[j] Lx[k] + Ly[j] Ly[k] for k >= j (all 45 written out as there)
+ *   6. with h'8 = 1: LtL[0:8,0:8] h' = -LtL[0:8,8] solved by LDL^T without square roots and
+ *      without pivoting (the recurrences, operation by operation: csrc/hg_refit.hpp).  This
+ *      replaces the reference's 9 x 9 eigen-decomposition; in normalised coordinates h'8
+ *      vanishes only when the source centroid maps to infinity, which this form cannot fit.
+ *   7. H = T2^-1 H' T1 as the reference denormalises, then times 1 / H[8]
+ *   8. H64 (pairs,9; NULL skips it; 8-B aligned) takes the unrounded values, H (pairs,9; 4-B
+ *      aligned) each element rounded once to binary32 (H[8] is 1.0f).  used[j] = n.
+ * A pair FAILS when n < 4, a d is 0, a pivot is not > 0, or an element of H64 -- or its
+ * binary32 rounding -- is not finite: then H holds nine quiet NaNs (0x7FC00000), H64 nine
+ * 0x7FF8000000000000, and used[j] is still n.  An empty pair fails with used 0.
+ *
+ * The order of the three sums is part of the definition: row i of the pair goes to lane
+ * i % 256, a lane adds its rows in ascending order into +0.0 (an unselected row adds +0.0),
+ * and the 256 lane sums v are combined by  for d = 1, 2, 4 ... 128: v[l] <- v[l] + v[l xor d].
+ * It depends only on the pair's row count and the row's index inside the pair -- not on
+ * `pairs`, the grid or other pairs -- so the result is deterministic and equals the numpy
+ * restatement (tests/restate_refit.py) bit for bit.
+ *
+ * 0 <= total < 2^31, pairs < 2^20; pairs == 0 is a no-op.  One launch on `stream`, one block per
+ * pair: nothing allocated, no workspace, no synchronisation, capturable in a hipGraph. */
+int hg_ransac_refit_f32(const float* pool_src, const float* pool_tar, int64_t total,
+                        const int64_t* pair_offsets, int64_t pairs, const uint8_t* mask,
+                        float* H, double* H64 /* nullable */, int32_t* used, void* stream);
+
+/* The re-mask step of a local-optimisation round, batched.  For pair j: count = inliers of
+ * H_new[j] (pairs,9) over the pair's rows by hg_ransac_score_f32's test, bit for bit.  When
+ * all nine elements of H_new[j] are finite AND count >= count_io[j]: H_io[j] = H_new[j],
+ * count_io[j] = count, and the pair's rows of mask_io become 1 / 0 by that test.  Otherwise
+ * all three are left untouched, so a round never lowers a pair's inlier count.  Same limits
+ * and conventions as hg_ransac_refit_f32; H_new, H_io, count_io 4-B aligned. */
+int hg_ransac_accept_f32(const float* H_new, const float* pool_src, const float* pool_tar,
+                         int64_t total, const int64_t* pair_offsets, int64_t pairs, float thresh,
+                         float* H_io, uint32_t* count_io, uint8_t* mask_io, void* stream);
+
 /* ---- The reference's Table-8 sampling pipeline in its own formats (hg_table8.hip) ----
  * GPU_Runtime Test.cu:1443-1451: 4*n MRG32K3A words, get_rand_list, cal_ACA/cal_SKS.
  * rand_list is (4,n) uint32 -- word k of hypothesis id at rand_list[id + k*n], as

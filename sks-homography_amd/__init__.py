@@ -21,9 +21,10 @@ from ._lib import HG_FLAG_NORMALIZE, HG_LAYOUT_AOS, HG_LAYOUT_SOA, HipError, lib
 from .ops import (aca, aca_backward, aca_vanilla, fill_uniform, sks, solve, solve_grouped, solve_host, stream_copy, tensor_aca_rect,
                   tensor_aca_rect_autograd, tensor_aca_rect_backward,
                   tensor_aca_offsets, tensor_aca_offsets_backward)
-from .ransac import (ConsensusResult, RansacResult, fill_bits, gather_solve, get_rand_list,
-                     inlier_mask, mrg32k3a_state, rand_gather_solve, rand_mrg32k3a, ransac,
-                     ransac_consensus, read_points, sample_solve, sample_solve_seeded)
+from .ransac import (ConsensusResult, RansacResult, RefitResult, fill_bits, gather_solve,
+                     get_rand_list, inlier_mask, mrg32k3a_state, rand_gather_solve, rand_mrg32k3a,
+                     ransac, ransac_consensus, read_points, refit, sample_solve,
+                     sample_solve_seeded)
 from .ransac import score as ransac_score
 from .reference_api import ACA_vanilla, TensorACA_rect, adjust, getInput, getTar
 from .shard import gather_blocks, scatter_blocks, shard_range
@@ -36,7 +37,7 @@ __all__ = [
     "tensor_aca_rect_backward", "tensor_aca_offsets", "tensor_aca_offsets_backward",
     "fill_uniform", "sample_solve", "sample_solve_seeded", "fill_bits", "ransac", "ransac_score", "RansacResult", "stream_copy",
     "read_points", "rand_mrg32k3a", "get_rand_list", "gather_solve", "rand_gather_solve",
-    "mrg32k3a_state", "ransac_consensus", "inlier_mask", "ConsensusResult",
+    "mrg32k3a_state", "ransac_consensus", "inlier_mask", "ConsensusResult", "refit", "RefitResult",
     "TensorACA_rect", "ACA_vanilla", "getInput", "getTar", "adjust", "shard_range",
     "gather_blocks", "scatter_blocks", "lib", "version", "HipError", "HG_LAYOUT_AOS", "HG_LAYOUT_SOA",
     "HG_FLAG_NORMALIZE", "BYTES_PER_PROBLEM", "RECT_BYTES_PER_PROBLEM",

@@ -68,6 +68,9 @@ SIGNATURES = {
     "hg_ransac_consensus_f32": ([_vp, _vp, _i64, _vp, _i64, _i64, ctypes.c_float, ctypes.c_uint64,
                                  ctypes.c_uint64, _int, _vp, _vp, _vp, _vp, _vp, _vp], _int),
     "hg_ransac_inlier_mask_f32": ([_vp, _vp, _vp, ctypes.c_uint32, ctypes.c_float, _vp, _vp], _int),
+    "hg_ransac_refit_f32": ([_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp], _int),
+    "hg_ransac_accept_f32": ([_vp, _vp, _vp, _i64, _vp, _i64, ctypes.c_float, _vp, _vp, _vp, _vp],
+                             _int),
     "hg_rand_mrg32k3a_u32": ([_vp, _i64, ctypes.c_uint64, _vp], _int),
     "hg_mrg32k3a_state": ([ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, _vp], _int),
     "hg_rand_gather_solve_f64": ([_int, _vp, _vp, ctypes.c_uint32, ctypes.c_uint64, _vp, _i64, _int,

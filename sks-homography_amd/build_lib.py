@@ -25,8 +25,8 @@ TUNE_LIB = os.path.join(LIB_DIR, "libsks_homography_tune.so")
 MULTI_LIB = os.path.join(LIB_DIR, "libsks_homography_multi.so")
 ARCH = os.environ.get("SKS_AMD_ARCH", "gfx950")
 
-SOURCES = ["hg_kernels.hip", "hg_ransac.hip", "hg_consensus.hip", "hg_table8.hip", "hg_sks_api.cpp",
-           "hg_host.cpp"]
+SOURCES = ["hg_kernels.hip", "hg_ransac.hip", "hg_consensus.hip", "hg_refit.hip", "hg_table8.hip",
+           "hg_sks_api.cpp", "hg_host.cpp"]
 # kernel-variant sweeps and timing loops (tools/, tests): a separate library so the product
 # library carries only the shipped kernels
 TUNE_SOURCES = ["hg_tune.hip"]

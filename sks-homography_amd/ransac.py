@@ -271,9 +271,67 @@ def _pair_pools(pool_src: torch.Tensor, pool_tar: torch.Tensor):
         raise ValueError("the pools must hold fewer than 2^31 points")
 
 
+def _pair_offsets(pair_offsets, total: int):
+    """pair_offsets as ransac_consensus takes them (None, a list, a host or a device int64
+    tensor), checked but not yet moved: a 1-D int64 tensor."""
+    if pair_offsets is None:
+        pair_offsets = [0, total]
+    if not isinstance(pair_offsets, torch.Tensor):
+        pair_offsets = torch.tensor([int(v) for v in pair_offsets], dtype=torch.int64)
+    if pair_offsets.dim() != 1 or pair_offsets.numel() < 1 or pair_offsets.dtype != torch.int64:
+        raise ValueError("pair_offsets must be a 1-D int64 tensor (or a list) of pairs + 1 "
+                         f"offsets, got {tuple(pair_offsets.shape)} {pair_offsets.dtype}")
+    return pair_offsets
+
+
+def _offsets_on(pair_offsets: torch.Tensor, dev) -> torch.Tensor:
+    if pair_offsets.device != dev:
+        if pair_offsets.is_cuda:
+            raise ValueError(f"tensors on different devices: {dev} vs {pair_offsets.device}")
+        pair_offsets = pair_offsets.to(dev)
+    return pair_offsets.contiguous()
+
+
+class RefitResult(NamedTuple):
+    H: torch.Tensor          # (pairs,9) float32: least-squares H of each pair's selected rows
+    used: torch.Tensor       # (pairs,) int32: how many rows the mask selected
+    H64: torch.Tensor = None  # (pairs,9) float64: the same before rounding (return_f64=True)
+
+
+def refit(pool_src: torch.Tensor, pool_tar: torch.Tensor, mask: torch.Tensor, pair_offsets=None,
+          return_f64: bool = False) -> RefitResult:
+    """Least-squares refit (N-point DLT, hg_ransac_refit_f32) of every pair's selected rows.
+
+    Pools and ``pair_offsets`` as ``ransac_consensus``; ``mask`` is a (total,) uint8 device
+    tensor and any non-zero byte selects its row -- a consensus mask as it stands.  In binary64
+    and in a fixed summation order (include/sks_homography.h), so the result is deterministic
+    and independent of the batch.  A pair that cannot be fitted (fewer than 4 rows selected,
+    degenerate points, a non-finite result) gets a NaN H; ``used`` still counts its rows.
+    Everything returned is a device tensor; nothing synchronises."""
+    _pair_pools(pool_src, pool_tar)
+    total = pool_src.shape[0]
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or mask.shape != (total,):
+        raise ValueError(f"mask must be a ({total},) uint8 tensor, got "
+                         f"{tuple(mask.shape) if isinstance(mask, torch.Tensor) else type(mask)} "
+                         f"{getattr(mask, 'dtype', '')}")
+    pair_offsets = _pair_offsets(pair_offsets, total)
+    dev = _require_device(pool_src, pool_tar, mask)
+    off = _offsets_on(pair_offsets, dev)
+    pairs = off.numel() - 1
+    ps, pt, mk = _pool(pool_src), _pool(pool_tar), mask.contiguous()
+    H = torch.empty((pairs, 9), dtype=torch.float32, device=dev)
+    used = torch.empty(pairs, dtype=torch.int32, device=dev)
+    H64 = torch.empty((pairs, 9), dtype=torch.float64, device=dev) if return_f64 else None
+    with _guard(dev):
+        _lib.call("hg_ransac_refit_f32", ps.data_ptr(), pt.data_ptr(), total, off.data_ptr(), pairs,
+                  mk.data_ptr(), H.data_ptr(), H64.data_ptr() if return_f64 else None,
+                  used.data_ptr(), _stream(dev))
+    return RefitResult(H, used, H64)
+
+
 def ransac_consensus(pool_src: torch.Tensor, pool_tar: torch.Tensor, hypotheses: int,
                      thresh: float, pair_offsets=None, seed: int = 11, offset: int = 0,
-                     algo: str = "aca", mask: bool = True) -> ConsensusResult:
+                     algo: str = "aca", mask: bool = True, refine: int = 0) -> ConsensusResult:
     """RANSAC consensus of many image pairs in one device pass (hg_ransac_consensus_f32).
 
     The pools hold every pair's correspondences back to back; pair j owns rows
@@ -283,32 +341,32 @@ def ransac_consensus(pool_src: torch.Tensor, pool_tar: torch.Tensor, hypotheses:
     ``ransac(pool_j, ..)`` made with stream offset ``offset + 4 * hypotheses * j``, bit for
     bit, and ``mask`` marks the pair's inliers of its H (all zero when ``mask=False``).  An
     empty pair gives NaN H, 0 inliers, index 0.  Everything returned is a device tensor;
-    nothing synchronises, so the call can be captured in a graph."""
+    nothing synchronises, so the call can be captured in a graph.
+
+    ``refine=R`` (needs ``mask=True``) then runs R local-optimisation rounds on those outputs,
+    still on the device: ``refit`` on each pair's inliers, and hg_ransac_accept_f32, which
+    re-masks with the refitted H and keeps it where it counts no fewer inliers.  H, inliers
+    and mask are then the accepted ones (inliers never falls from round to round); index is
+    still the winning hypothesis.  ``refine=0`` makes exactly the calls made without it."""
     _pair_pools(pool_src, pool_tar)
     if algo not in ("aca", "sks"):
         raise ValueError(f"algo must be 'aca' or 'sks', got {algo!r}")
     if not 1 <= hypotheses <= 1 << 31:
         raise ValueError(f"hypotheses must be in [1, 2^31], got {hypotheses}")
+    if not isinstance(refine, int) or isinstance(refine, bool) or refine < 0:
+        raise ValueError(f"refine must be an integer >= 0, got {refine!r}")
+    if refine and not mask:
+        raise ValueError("refine > 0 refits the inliers the mask marks: it requires mask=True")
     total = pool_src.shape[0]
-    if pair_offsets is None:
-        pair_offsets = [0, total]
-    if not isinstance(pair_offsets, torch.Tensor):
-        pair_offsets = torch.tensor([int(v) for v in pair_offsets], dtype=torch.int64)
+    pair_offsets = _pair_offsets(pair_offsets, total)
     # offsets known on the host that rise from <= 0 to >= total give every row to one pair:
     # the kernel then writes the whole mask, and it need not be cleared first
     tiled = False
-    if mask and pair_offsets.dim() == 1 and pair_offsets.numel() and not pair_offsets.is_cuda:
+    if mask and not pair_offsets.is_cuda:
         v = pair_offsets.tolist()
         tiled = v[0] <= 0 and v[-1] >= total and all(a <= b for a, b in zip(v, v[1:]))
-    if pair_offsets.dim() != 1 or pair_offsets.numel() < 1 or pair_offsets.dtype != torch.int64:
-        raise ValueError("pair_offsets must be a 1-D int64 tensor (or a list) of pairs + 1 "
-                         f"offsets, got {tuple(pair_offsets.shape)} {pair_offsets.dtype}")
     dev = _require_device(pool_src, pool_tar)
-    if pair_offsets.device != dev:
-        if pair_offsets.is_cuda:
-            raise ValueError(f"tensors on different devices: {dev} vs {pair_offsets.device}")
-        pair_offsets = pair_offsets.to(dev)
-    off = pair_offsets.contiguous()
+    off = _offsets_on(pair_offsets, dev)
     pairs = off.numel() - 1
     ps, pt = _pool(pool_src), _pool(pool_tar)
     H = torch.empty((pairs, 9), dtype=torch.float32, device=dev)
@@ -324,6 +382,16 @@ def ransac_consensus(pool_src: torch.Tensor, pool_tar: torch.Tensor, hypotheses:
                   pairs, hypotheses, float(thresh), seed, offset, 0 if algo == "aca" else 1,
                   H.data_ptr(), inliers.data_ptr(), index.data_ptr(),
                   out_mask.data_ptr() if mask else None, work.data_ptr(), _stream(dev))
+        if refine:
+            H_new = torch.empty((pairs, 9), dtype=torch.float32, device=dev)
+            used = torch.empty(pairs, dtype=torch.int32, device=dev)
+        for _ in range(refine):
+            _lib.call("hg_ransac_refit_f32", ps.data_ptr(), pt.data_ptr(), total, off.data_ptr(),
+                      pairs, out_mask.data_ptr(), H_new.data_ptr(), None, used.data_ptr(),
+                      _stream(dev))
+            _lib.call("hg_ransac_accept_f32", H_new.data_ptr(), ps.data_ptr(), pt.data_ptr(), total,
+                      off.data_ptr(), pairs, float(thresh), H.data_ptr(), inliers.data_ptr(),
+                      out_mask.data_ptr(), _stream(dev))
     return ConsensusResult(H, inliers, index, out_mask)
 
 
